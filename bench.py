@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- YOLOv4 608x608 forward images/sec on N MI355X (one process per GPU).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N
           --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...)
 
@@ -15,7 +15,15 @@ PCIe-inclusive rate (H2D input + D2H heads) is reported beside it as
 `e2e_images_per_sec`, never as `value`.  Ranks are independent replicas on
 disjoint image shards (no data-path collective): scaling = weak.
 
-The JSON line also carries
+A plain run sets up, warms up, times K steps and prints the JSON line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step, and the workload's
+description).  --dump-outputs DIR then also writes the decoded YOLO heads of the last timed step
+(rank 0's shard): DIR/head_<layer>.npy, float32 [batch, outputs], the arrays DkLayerOutput hands a
+caller.  When the heads together exceed DUMP_BUDGET_BYTES, every head is replaced by the same fraction
+of its values, a 1-D array at sorted flat positions drawn with a fixed seed from its size alone, so two
+runs with the same arguments write the same elements.  Inputs and weights are seeded (tools/synth.py).
+
+--full adds the PCIe-inclusive rates (e2e_*) and these fields:
   roofline      -- the dominant conv kernel (the instantiation with the largest share of
                    the step): ALGORITHMIC FLOPs per launch (the reference's counter
                    2*nweights*oh*ow*batch, src/convolutional_layer.cpp:714 = SURVEY 8d)
@@ -41,6 +49,7 @@ import argparse
 import ctypes as C
 import json
 import os
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -54,6 +63,8 @@ FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: Peak FP32 (matrix), dense
 FP16_MFMA_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: Peak BF16/FP16 MFMA, dense (not the 2:1-sparse figure)
 CFG = "yolov4"
 BATCH_PER_GPU = 16
+DUMP_BUDGET_BYTES = 60 * 10 ** 6  # --dump-outputs writes at most this many bytes (yolov4 b=16 heads: 124 MB)
+DUMP_SEED = 2024
 
 
 def lib_sha16():
@@ -106,6 +117,22 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+def dump_heads(net, outdir):
+    """--dump-outputs: the decoded YOLO heads now in HBM as DIR/head_<layer>.npy (module docstring)."""
+    import numpy as np
+    heads = [i for i in range(net.n) if net.info(i)["type"] == 17]  # YOLO (LAYER_TYPE, yolo_core.h)
+    total = sum(4 * net.info(i)["batch"] * net.info(i)["outputs"] for i in heads)
+    frac = min(1.0, DUMP_BUDGET_BYTES / float(total))
+    os.makedirs(outdir, exist_ok=True)
+    for i in heads:
+        out = net.output(i)  # D2H copy of the head after NetworkSync
+        if frac < 1.0:
+            k = int(out.size * frac)
+            pos = np.sort(np.random.default_rng([DUMP_SEED, out.size]).choice(out.size, k, replace=False))
+            out = out.ravel()[pos]
+        np.save(os.path.join(outdir, "head_%d.npy" % i), np.ascontiguousarray(out, np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -117,7 +144,12 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--half", action="store_true", help="fp16 operands / fp32 accumulate on the layers the reference's rule admits (config C5)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short C2 / C4 / C5 legs of the N = 1 line")
+    ap.add_argument("--full", action="store_true",
+                    help="also the PCIe-inclusive rates, the dominant kernel's roofline, the CPU baseline and the other configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the decoded heads of the last timed step to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # N > 1 without a launcher: start the N ranks ourselves as fresh child processes (one per GPU,
     # rendezvous on 127.0.0.1) BEFORE anything here touches the GPU, relay rank 0's JSON line and
@@ -192,70 +224,76 @@ def main():
     dt = time.perf_counter() - t0
     value, tmax = dkdist.aggregate_throughput(ctx, args.batch * args.steps, dt)
 
-    # ---- PCIe-inclusive rate (reported beside, never as value) --------------
-    L.DkSetPullHeads(1)
-    e2e_steps = max(3, args.steps // 3)
-    net.predict(x)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(e2e_steps):
-        net.predict(x)  # H2D input, forward, D2H heads, sync
-    e2e_dt = time.perf_counter() - t0
-    e2e, _ = dkdist.aggregate_throughput(ctx, args.batch * e2e_steps, e2e_dt)
+    if args.dump_outputs and ctx.rank == 0:
+        dump_heads(net, args.dump_outputs)
 
-    # the same frames -> heads path with the input step taken off the critical path (DkNetworkStageFloat: the next
-    # batch's pinned copy + H2D run on the staging stream under the current forward; heads still cross PCIe whole)
-    def f32_step():
-        net.predict_staged()
+    # ---- everything below is --full only ---------------------------------------
+    e2e = e2e_staged = e2e_u8 = None
+    if args.full:
+        # ---- PCIe-inclusive rate (reported beside, never as value) --------------
+        L.DkSetPullHeads(1)
+        e2e_steps = max(3, args.steps // 3)
+        net.predict(x)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(e2e_steps):
+            net.predict(x)  # H2D input, forward, D2H heads, sync
+        e2e_dt = time.perf_counter() - t0
+        e2e, _ = dkdist.aggregate_throughput(ctx, args.batch * e2e_steps, e2e_dt)
+
+        # the same frames -> heads path with the input step taken off the critical path (DkNetworkStageFloat: the next
+        # batch's pinned copy + H2D run on the staging stream under the current forward; heads still cross PCIe whole)
+        def f32_step():
+            net.predict_staged()
+            net.stage_float(x)
+            net.collect()
         net.stage_float(x)
-        net.collect()
-    net.stage_float(x)
-    f32_step()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(e2e_steps):
         f32_step()
-    e2e_staged_dt = time.perf_counter() - t0
-    e2e_staged, _ = dkdist.aggregate_throughput(ctx, args.batch * e2e_steps, e2e_staged_dt)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(e2e_steps):
+            f32_step()
+        e2e_staged_dt = time.perf_counter() - t0
+        e2e_staged, _ = dkdist.aggregate_throughput(ctx, args.batch * e2e_steps, e2e_staged_dt)
 
-    # ---- u8 frames in, detections out (Mat2Image and the candidate extraction on
-    # the device: bytes cross PCIe one way, a few candidate records the other) ----------------
-    # synthetic weights have no meaningful confidence scale: pick the threshold that lets
-    # ~200 predictors per image through (a busy real scene), from the heads just pulled
-    obj = []
-    for i in range(net.n):
-        f = net.info(i)
-        if f["type"] == 17:  # YOLO (LAYER_TYPE, yolo_core.h)
-            o = net.output(i)[0].reshape(f["n"], 5 + f["classes"], -1)
-            obj.append(o[:, 4, :].ravel())
-    obj = np.sort(np.concatenate(obj))
-    box_thresh = float(obj[-201]) if obj.size > 201 else 0.25
-    L.DkSetPullHeads(0)
-    frames = (np.clip(x.reshape(args.batch, net.c, net.h, net.w), 0, 1) * 255).astype(np.uint8)
-    frames = np.ascontiguousarray(frames.transpose(0, 2, 3, 1))
+        # ---- u8 frames in, detections out (Mat2Image and the candidate extraction on
+        # the device: bytes cross PCIe one way, a few candidate records the other) ----------------
+        # synthetic weights have no meaningful confidence scale: pick the threshold that lets
+        # ~200 predictors per image through (a busy real scene), from the heads just pulled
+        obj = []
+        for i in range(net.n):
+            f = net.info(i)
+            if f["type"] == 17:  # YOLO (LAYER_TYPE, yolo_core.h)
+                o = net.output(i)[0].reshape(f["n"], 5 + f["classes"], -1)
+                obj.append(o[:, 4, :].ravel())
+        obj = np.sort(np.concatenate(obj))
+        box_thresh = float(obj[-201]) if obj.size > 201 else 0.25
+        L.DkSetPullHeads(0)
+        frames = (np.clip(x.reshape(args.batch, net.c, net.h, net.w), 0, 1) * 255).astype(np.uint8)
+        frames = np.ascontiguousarray(frames.transpose(0, 2, 3, 1))
 
-    # double-buffered input step: while the forward of batch k runs, batch k+1 is copied to pinned memory
-    # and crosses PCIe on the copy stream (DkNetworkStageU8); the boxes of batch k are collected after that
-    def u8_step():
-        net.predict_staged()      # device Mat2Image of the staged frames + forward (asynchronous)
-        net.stage_u8(frames)      # next batch: host copy + H2D, overlapped with the forward above
-        n = 0
-        for b in range(args.batch):
-            n += len(net.boxes(b, box_thresh, max_dets=2048)[0])
-        return n
+        # double-buffered input step: while the forward of batch k runs, batch k+1 is copied to pinned memory
+        # and crosses PCIe on the copy stream (DkNetworkStageU8); the boxes of batch k are collected after that
+        def u8_step():
+            net.predict_staged()      # device Mat2Image of the staged frames + forward (asynchronous)
+            net.stage_u8(frames)      # next batch: host copy + H2D, overlapped with the forward above
+            n = 0
+            for b in range(args.batch):
+                n += len(net.boxes(b, box_thresh, max_dets=2048)[0])
+            return n
 
-    net.stage_u8(frames)
-    u8_step()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(e2e_steps):
-        ndet = u8_step()
-    u8_dt = time.perf_counter() - t0
-    e2e_u8, _ = dkdist.aggregate_throughput(ctx, args.batch * e2e_steps, u8_dt)
+        net.stage_u8(frames)
+        u8_step()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(e2e_steps):
+            ndet = u8_step()
+        u8_dt = time.perf_counter() - t0
+        e2e_u8, _ = dkdist.aggregate_throughput(ctx, args.batch * e2e_steps, u8_dt)
 
     # ---- roofline of the dominant kernel: HIP events per conv launch ---------
     roofline = None
-    if ctx.rank == 0:
+    if args.full and ctx.rank == 0:
         L.DkSetPullHeads(0)
         L.dk_profile_enable(1)
         prof_steps = 3
@@ -314,7 +352,7 @@ def main():
 
     # ---- CPU baseline on the host cores (rank 0, N = 1 only) -----------------
     cpu_baseline = None
-    if ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline:
+    if args.full and ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline:
         def cpu_leg(cfg_name, w, seconds, threads=None):
             env = dict(os.environ)
             if threads:
@@ -336,7 +374,7 @@ def main():
     # ---- the other BASELINE GPU configs, a few seconds each (N = 1 line of the headline workload only): child
     # processes of this script / tools/bench_train.py after this process has released the GPU work above
     other = None
-    if (ctx.rank == 0 and ctx.world == 1 and args.cfg == CFG and args.batch == BATCH_PER_GPU and not args.half
+    if (args.full and ctx.rank == 0 and ctx.world == 1 and args.cfg == CFG and args.batch == BATCH_PER_GPU and not args.half
             and not args.no_other_configs):
         def leg(cmd):
             try:
@@ -350,7 +388,7 @@ def main():
             except Exception as e:
                 return {"error": str(e)[:200]}
         me = os.path.abspath(__file__)
-        common = ["--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-other-configs"]
+        common = ["--steps", "20", "--warmup", "3", "--full", "--no-cpu-baseline", "--no-other-configs"]
         net.close()   # (12 GB of activations: the legs get the whole card)
         net = None
         other = {
@@ -376,20 +414,24 @@ def main():
             "frac_of_fp32_mfma_roofline": value * 128.459e9 / (ctx.world * FP32_MFMA_PEAK_TFLOPS * 1e12)
             if args.cfg == "yolov4" else None,
             "gflop_per_image": {"yolov4": 128.459, "yolov4-tiny": 6.910, "yolov4-csp": 77.003}.get(args.cfg),
-            "e2e_images_per_sec": e2e,
-            "e2e_staged_float_frames_images_per_sec": e2e_staged,
-            "e2e_u8_frames_to_boxes_images_per_sec": e2e_u8,
-            "e2e_u8_note": "u8 HWC frames -> device Mat2Image -> forward -> device candidate compaction -> "
-                           "Detection arrays for every image; threshold passes %.0f predictors/image" % (ndet / args.batch),
             "load_seconds_incl_autotune": load_seconds,
             "lib_sha16": lib_sha16(),
-            "roofline": roofline,
-            "cpu_baseline": cpu_baseline,
-            "other_configs": other,
         }
+        if args.full:
+            res.update({
+                "e2e_images_per_sec": e2e,
+                "e2e_staged_float_frames_images_per_sec": e2e_staged,
+                "e2e_u8_frames_to_boxes_images_per_sec": e2e_u8,
+                "e2e_u8_note": "u8 HWC frames -> device Mat2Image -> forward -> device candidate compaction -> "
+                               "Detection arrays for every image; threshold passes %.0f predictors/image" % (ndet / args.batch),
+                "roofline": roofline,
+                "cpu_baseline": cpu_baseline,
+                "other_configs": other,
+            })
         print(json.dumps(res), flush=True)
     if net is not None:
         net.close()
+    shutil.rmtree(tmp, ignore_errors=True)
     ctx.close()
 
 

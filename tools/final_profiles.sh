@@ -9,9 +9,9 @@ cd $R
 for t in $TAGS; do
   case $t in
     c3) args="" ;;
-    c2) args="bench.py --cfg yolov4-tiny --batch 32 --steps 20 --warmup 3 --no-cpu-baseline --no-other-configs" ;;
-    c5) args="bench.py --cfg yolov4-csp --batch 32 --half --steps 20 --warmup 3 --no-cpu-baseline --no-other-configs" ;;
-    c5x) args="bench.py --cfg yolov4x-mish --batch 32 --half --steps 20 --warmup 3 --no-cpu-baseline --no-other-configs" ;;
+    c2) args="bench.py --cfg yolov4-tiny --batch 32 --steps 20 --warmup 3 --full --no-cpu-baseline --no-other-configs" ;;
+    c5) args="bench.py --cfg yolov4-csp --batch 32 --half --steps 20 --warmup 3 --full --no-cpu-baseline --no-other-configs" ;;
+    c5x) args="bench.py --cfg yolov4x-mish --batch 32 --half --steps 20 --warmup 3 --full --no-cpu-baseline --no-other-configs" ;;
     c4) args="tools/bench_train.py --steps 5 --warmup 2" ;;
   esac
   timeout -k 10 1000 bash tools/make_profiles.sh gpurun_out/$NAME/$t $args > gpurun_out/$NAME.$t.log 2>&1

@@ -12,8 +12,8 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $R/$OUT
 cd /tmp && export TMPDIR=/tmp
 export DK_TUNE_FILE=$R/$OUT/tune.txt
-python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $R/$OUT/warm.json 2> $R/$OUT/warm.err
+python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline > $R/$OUT/warm.json 2> $R/$OUT/warm.err
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $R/$OUT/$c -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $R/$OUT/$c.log 2>&1
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $R/$OUT/$c -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $R/$OUT/$c.log 2>&1
 done
 python3 $R/tools/pmc_summarize.py $R/$OUT
